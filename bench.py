@@ -7,7 +7,10 @@ frozen, eval) -> halved student (d88/h2/16L) FM distillation, ver5 heads, 16 kHz
 fp32 storage, dropout 0.1, SpecAugment and dither on, AdamW + Noam.  A step is one full
 forward + backward + (RCCL all-reduce) + optimizer update over one batch.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0;
+`--dump-outputs DIR` also writes what the last timed step computed.  `--full` adds everything that
+takes runs of its own -- the per-kernel roofline figures, the CPU baseline, the sensitivity runs -- to
+the same line.
 """
 from __future__ import annotations
 
@@ -58,6 +61,8 @@ FAMILY_KERNELS = {"ffn_fwd": ("ffn_fwd_kernel",), "ffn_bwd": ("ffn_bwd_kernel",)
 # FFN dense contractions (student fwd+bwd + teacher fwd), the north-star MFMA roofline subject
 STEP_GFLOP_PER_UTT = 62.6
 ATTN_FFN_GFLOP_PER_UTT = 23.0
+# --dump-outputs: at most this many bytes in all; a larger array is written as a fixed, seeded sample
+DUMP_MAX_BYTES = 64 * 1000 * 1000
 
 
 def _is_call_kernel(stem):
@@ -112,17 +117,25 @@ def _family_stems(fam):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=B_PER_GPU)
     ap.add_argument("--samples", type=int, default=N_SAMPLES)
     ap.add_argument("--math", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the loss vector it returns, the "
+                         "updated student parameters and their gradient) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline figure: the per-kernel "
+                         "roofline lines (an instrumented step of their own), the CPU baseline and the sensitivity "
+                         "runs (f32, V=1024, encoder-level FM, FastConformer-XL bf16 / fp8)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads for the CPU baseline (default: every core this process may use, its "
                          "affinity set capped by the cgroup CPU quota; os.cpu_count() is reported beside it)")
     ap.add_argument("--no-f32-sensitivity", action="store_true",
-                    help="skip the --math f32 sensitivity measurement (the reference trains fp32)")
+                    help="with --full: skip the --math f32 and the other sensitivity measurements (the reference "
+                         "trains fp32)")
     ap.add_argument("--deterministic", action="store_true",
                     help="ordered reductions everywhere (bitwise-reproducible steps; kdfm_set_deterministic)")
     ap.add_argument("--eager", action="store_true",
@@ -131,7 +144,10 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one captured HIP graph (measured slower: hipGraph replay ran the "
                          "teacher / weight-gradient / CTC streams serially, 43.9 vs 40.1 ms/step eager)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def attn_ffn_gflop_per_utt(cfg, samples):
@@ -331,6 +347,199 @@ def launch_ranks(args, argv, run=None) -> int | None:
     return (run or subprocess.call)(cmd)
 
 
+def dump_outputs(out_dir, eng, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what a caller of the timed step holds after the last one, as float32 `<name>.npy`:
+    `losses` (the vector the step returns: total, ctc, kl, recon, layer KD), `student_params` (the flat
+    student parameter buffer after the AdamW update) and `student_grad` (the flat gradient that update
+    consumed).  The arrays share `max_bytes` equally; a larger one is written as the elements at a fixed
+    set of sorted indices drawn with numpy's default_rng(0), the same for every run of the same shape.
+    Inputs, weights and the device RNG are seeded, so two runs with the same arguments compute the same
+    step; the default schedule's unordered (atomic) reductions leave rounding-level differences between
+    them (measured after 55 steps: parameters 1e-4, gradient 5e-4 relative L2); --deterministic orders the reductions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    outs = {"losses": eng.losses, "student_params": eng.student.data, "student_grad": eng.student.grad}
+    cap = max_bytes // len(outs) // 4
+    for name, t in outs.items():
+        a = t.detach().to(torch.float32).cpu().numpy().reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def trace_step(args, eng, batch, ar):
+    """--full: live per-kernel timing over the schedule that was timed: a second step plan
+    recorded with every traced launch -- each kdfm_gemm launch (keyed by the kernel family libkdfm routed it to),
+    the fused kernels, the frontend, the depthwise convs -- bracketed by HIP events on the stream it runs on.  The
+    events are part of that plan (each replay re-records them in place), so the durations come from a REPLAYED step
+    with the same four-stream overlap and contention as the timed ones (the round-5 line took them from an eager
+    instrumented step: 1.3x more optimistic than the rocprof summary of the replayed step).  Eager / graph issue:
+    one instrumented eager step.  Returns (the trace, how its step was issued)."""
+    from kdfm import kernels as K
+    trace = K.Trace(["*", "frontend", "dwconv", "ffn_fwd", "ffn_bwd", "wgrad_bf16", "wgrad_fold", "attn_fwd", "attn_prep",
+                     "attn_bwd"])
+    trace_issue = "eager instrumented step"
+    if not args.eager and not args.graph:
+        with trace:
+            tplan = eng.make_plan(*batch, ar)
+        tplan.replay()   # one warm replay; the events keep the timestamps of the last one
+        torch.cuda.synchronize()
+        tplan.replay()
+        trace_issue = f"replayed step plan with per-launch HIP events ({len(tplan)} ops)"
+    else:
+        with trace:
+            eng.train_step(*batch, ar)
+    torch.cuda.synchronize()
+    losses = eng.losses.detach().cpu().tolist()
+    if not all(math.isfinite(x) for x in losses):
+        raise RuntimeError(f"non-finite losses after the instrumented step: {losses}")
+    return trace, trace_issue
+
+
+def full_report(args, cfg, eng, dev, world, trace, trace_issue):
+    """--full, rank 0: the result line's entries beyond the headline figure -- the roofline lines from the
+    instrumented step's trace, then (one GPU only) the CPU baseline and the sensitivity runs."""
+    tsum = trace.summary()
+    empty = {"launches": 0, "ms_total": 0.0, "flops_total": 0.0, "bytes_total": 0.0}
+    bf16_peak = MI355X_BF16_DENSE_TFLOPS if cfg.math == "bf16" else MI355X_F32_MFMA_TFLOPS
+
+    def rate(t):
+        n = max(1, t["launches"])
+        ms = t["ms_total"] / n
+        gbps = (t["bytes_total"] / n) / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+        tfl = (t["flops_total"] / n) / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        return n, ms, gbps, tfl
+
+    routes = {k[5:]: v for k, v in tsum.items() if k.startswith("gemm:")}
+    # the row-parallel weight gradients run both inside kdfm_gemm (f32 operands) and as kdfm_wgrad_bf16
+    # (bf16 operands): one kernel family
+    if "wgrad_bf16" in tsum:
+        w = dict(routes.get("wgrad_rows", empty))
+        for k in ("launches", "ms_total", "flops_total", "bytes_total"):
+            w[k] = w.get(k, 0) + tsum["wgrad_bf16"][k]
+        # deferred folds (kdfm_wgrad_fold_flush: one batched launch per encoder layer) run outside the
+        # products' traced calls: their time joins the family, not their launch count (a call stays one
+        # product + its fold)
+        if "wgrad_fold" in tsum:
+            w["ms_total"] += tsum["wgrad_fold"]["ms_total"]
+        routes["wgrad_rows"] = w
+    for fam in ("ffn_fwd", "ffn_bwd", "attn_fwd", "attn_prep", "attn_bwd"):
+        if fam in tsum:
+            routes[fam] = tsum[fam]
+    by_route = {}
+    for r, t in sorted(routes.items(), key=lambda kv: -kv[1]["ms_total"]):
+        n, ms, gbps, tfl = rate(t)
+        by_route[r] = {"launches": n, "ms_per_step": round(t["ms_total"], 3), "avg_ms": round(ms, 5),
+                       "GB_per_s": round(gbps, 1), "TFLOP_per_s": round(tfl, 2),
+                       "bytes_per_launch": round(t["bytes_total"] / n, 1),
+                       "flops_per_launch": round(t["flops_total"] / n, 1),
+                       "profile_ms_per_step": profile_ms(_family_stems(r))}
+    dom = next(iter(by_route)) if by_route else "generic"
+    dt = routes.get(dom, empty)
+    n, ms, gbps, tfl = rate(dt)
+    intensity = dt["flops_total"] / max(1.0, dt["bytes_total"])
+    ridge = bf16_peak * 1e12 / (MI355X_HBM_GBPS * 1e9)
+    if intensity < ridge:
+        roof = {"bound": "hbm", "achieved": round(gbps, 1), "peak": MI355X_HBM_GBPS, "unit": "GB/s",
+                "frac": round(gbps / MI355X_HBM_GBPS, 4)}
+    else:
+        roof = {"bound": "mfma", "achieved": round(tfl, 2), "peak": bf16_peak, "unit": "TFLOP/s",
+                "frac": round(tfl / bf16_peak, 4)}
+    stems = FAMILY_KERNELS.get(dom) or ROUTE_KERNELS.get(dom, (dom,))
+    roof.update({"traffic": pmc_traffic(stems),
+                 "traffic_source": os.path.relpath(PMC_TRAFFIC, ROOT) + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, "
+                                   "all of the family's kernels incl. folds, per call = per main-kernel launch)",
+                 "kernel": f"{dom} family ({', '.join(stems)}): the kernel family with the largest aggregated "
+                           f"time of the step (kdfm_gemm routes + the fused kernels, HIP events on their streams)",
+                 "timing_source": trace_issue,
+                 "profile_ms_per_step": profile_ms(_family_stems(dom)),
+                 "profile_source": (os.path.relpath(_summary_path(), ROOT) + " (rocprofv3 --kernel-trace of this "
+                                    "bench command, whole steps; tools/roofline_check.py)") if _summary_path() else None,
+                 "launches": n, "avg_ms": round(ms, 5), "bytes_per_launch": round(dt["bytes_total"] / n, 1),
+                 "flops_per_launch": round(dt["flops_total"] / n, 1),
+                 "arith_intensity_flop_per_byte": round(intensity, 2)})
+    # the critical path: the compute stream carries the student chain and the whole backward's data
+    # gradients (the teacher, weight gradients and CTC/KL overlap it on their own streams)
+    csum = trace.summary(stream=eng.compute_stream.cuda_stream)
+    croutes = {k[5:]: v for k, v in csum.items() if k.startswith("gemm:")}
+    for fam in ("ffn_fwd", "ffn_bwd", "attn_fwd", "attn_prep", "attn_bwd", "wgrad_bf16"):
+        if fam in csum:
+            croutes[fam] = csum[fam]
+    crit = None
+    if croutes:
+        cdom, ct = max(croutes.items(), key=lambda kv: kv[1]["ms_total"])
+        cn, cms, cgbps, ctfl = rate(ct)
+        cint = ct["flops_total"] / max(1.0, ct["bytes_total"])
+        cb = "hbm" if cint < ridge else "mfma"
+        crit = {"bound": cb, "achieved": round(cgbps if cb == "hbm" else ctfl, 2),
+                "peak": MI355X_HBM_GBPS if cb == "hbm" else bf16_peak, "unit": "GB/s" if cb == "hbm" else "TFLOP/s",
+                "frac": round((cgbps / MI355X_HBM_GBPS) if cb == "hbm" else (ctfl / bf16_peak), 4),
+                "kernel": f"{cdom} family: the most time on the compute (critical-path) stream",
+                "ms_per_step_on_stream": round(ct["ms_total"], 3), "launches": cn, "avg_ms": round(cms, 5),
+                "traffic": pmc_traffic(FAMILY_KERNELS.get(cdom) or ROUTE_KERNELS.get(cdom, (cdom,))),
+                "by_family_ms": {k: round(v["ms_total"], 3) for k, v in
+                                 sorted(croutes.items(), key=lambda kv: -kv[1]["ms_total"])}}
+    # MFMA rate of the attention / FFN kernels (the north-star MFMA subject) per family
+    mfma_fams = {}
+    for fam in ("ffn_fwd", "ffn_bwd", "attn_fwd", "attn_bwd"):
+        if fam in tsum:
+            n_, ms_, _, tfl_ = rate(tsum[fam])
+            mfma_fams[fam] = {"TFLOP_per_s": round(tfl_, 2), "frac_bf16_peak": round(tfl_ / bf16_peak, 5),
+                              "launches": n_, "avg_ms": round(ms_, 5),
+                              "flops_per_launch": round(tsum[fam]["flops_total"] / n_, 1)}
+    fe = rate(tsum.get("frontend", empty))
+    dw = rate(tsum.get("dwconv", empty))
+    cpu = None
+    if not args.no_cpu_baseline and world == 1:
+        # every core this process may use: its affinity set capped by the cgroup CPU quota (a host that shows
+        # 256 CPUs under a 16-CPU cpu.max: 256 threads under that quota stall for minutes).
+        # os.cpu_count() (the whole machine) is reported beside it
+        threads = args.cpu_threads or _usable_cpus()
+        cpu = cpu_baseline(threads, args.samples)
+        cpu["cgroup_cpu_max"] = _cgroup_cpu_max()
+    f32 = v1024 = encfm = xl = xl8 = None
+    if not args.no_f32_sensitivity and cfg.math == "bf16" and world == 1:
+        _progress("f32 sensitivity")
+        f32 = sensitivity(dev, args.samples, math="f32")
+        f32["dtype"] = "f32"
+        _progress("V=1024 sensitivity")
+        v1024 = sensitivity(dev, args.samples, vocab=1024)
+        _progress("encoder-level FM + router sensitivity")
+        encfm = sensitivity(dev, args.samples, kd_model="encfm")
+        encfm["note"] = ("the asr_train.py model family on the same workload: router + flow matching on every "
+                         "hooked layer pair instead of the ver5 latent heads; not the headline value")
+        _progress("FastConformer-XL shape sensitivity")
+        xl = sensitivity(dev, args.samples, **XL_SHAPES)
+        xl["note"] = ("BASELINE.json configs[4]'s layer shapes (FastConformer-XL: d_model 1024, 8 heads, head dim "
+                      "128, 24 layers, dw_striding x8, kernel 9, no xscaling) for student and teacher on the same "
+                      "16 s x B=32 workload, bf16 (the wide Linear products on the large-tile route, "
+                      "csrc/biggemm.hip); not the headline value")
+        _progress("FastConformer-XL fp8 sensitivity")
+        xl8 = sensitivity(dev, args.samples, linear_fp8=True, **XL_SHAPES)
+        xl8["note"] = ("configs[4] at its stated precision: the same XL step with the wide Linear products' forward "
+                       "and data gradients on MX fp8 operands (e4m3 with an e8m0 scale per 32 contraction "
+                       "elements, applied by the block-scaled MFMA v_mfma_scale_f32_16x16x128_f8f6f4); attention "
+                       "core and weight gradients bf16; not the headline value")
+    return {
+        "roofline": roof,
+        "roofline_by_family": by_route,
+        "roofline_critical_path": crit,
+        "mfma_attn_ffn_by_family": mfma_fams,
+        "mel_frontend_hbm": {"achieved": round(fe[2], 1), "unit": "GB/s", "peak": MI355X_HBM_GBPS,
+                             "frac": round(fe[2] / MI355X_HBM_GBPS, 4), "launches": fe[0], "avg_ms": round(fe[1], 5),
+                             "bytes": "4 B x (N samples + T x 80 mel) per utterance (1.54 MB at 16 s)"},
+        "dwconv_hbm": {"achieved": round(dw[2], 1), "unit": "GB/s", "peak": MI355X_HBM_GBPS,
+                       "frac": round(dw[2] / MI355X_HBM_GBPS, 4), "launches": dw[0], "avg_ms": round(dw[1], 5),
+                       "bytes": "read g + write y, 4 B x rows x d per launch"},
+        "cpu_baseline": cpu,
+        "f32_sensitivity": f32,
+        "vocab_1024_sensitivity": v1024,
+        "encoder_fm_router_sensitivity": encfm,
+        "xl_shape_sensitivity": xl,
+        "xl_fp8_sensitivity": xl8,
+    }
+
+
 def main():
     args = parse()
     rc = launch_ranks(args, sys.argv[1:])
@@ -403,158 +612,22 @@ def main():
     if os.environ.get("KDFM_PLAN_KNOCKOUT") and rank == 0:   # what-if probe (kdfm/plan.py): not a bench line
         print(f"KNOCKOUT {os.environ['KDFM_PLAN_KNOCKOUT']} ms_per_step {1e3 * elapsed / args.steps:.3f}", flush=True)
         return
-    # live per-kernel timing over the schedule that was timed: a second step plan recorded with
-    # every traced launch -- each kdfm_gemm launch (keyed by the kernel family libkdfm routed it to), the fused
-    # kernels, the frontend, the depthwise convs -- bracketed by HIP events on the stream it runs on.  The events
-    # are part of that plan (each replay re-records them in place), so the durations come from a REPLAYED step with
-    # the same four-stream overlap and contention as the timed ones (the round-5 line took them from an eager
-    # instrumented step: 1.3x more optimistic than the rocprof summary of the replayed step).  Eager / graph issue:
-    # one instrumented eager step.
-    trace = K.Trace(["*", "frontend", "dwconv", "ffn_fwd", "ffn_bwd", "wgrad_bf16", "wgrad_fold", "attn_fwd", "attn_prep",
-                     "attn_bwd"])
-    trace_issue = "eager instrumented step"
-    if not args.eager and not args.graph:
-        with trace:
-            tplan = eng.make_plan(wav, wl, tg, tl, ar)
-        tplan.replay()   # one warm replay; the events keep the timestamps of the last one
-        torch.cuda.synchronize()
-        tplan.replay()
-        trace_issue = f"replayed step plan with per-launch HIP events ({len(tplan)} ops)"
-    else:
-        with trace:
-            eng.train_step(wav, wl, tg, tl, ar)
-    torch.cuda.synchronize()
     losses = eng.losses.detach().cpu().tolist()
     if not all(math.isfinite(x) for x in losses):
         raise RuntimeError(f"non-finite losses after the timed steps: {losses}")
-    tsum = trace.summary()
-    # the plans keep their steps' activations alive: release them before the sensitivity engines are built
-    tplan = plan = run = None
-    torch.cuda.empty_cache()
-    empty = {"launches": 0, "ms_total": 0.0, "flops_total": 0.0, "bytes_total": 0.0}
+    if args.dump_outputs and rank == 0:   # before anything else steps the engine: the last TIMED step's results
+        dump_outputs(args.dump_outputs, eng)
+    trace = trace_issue = None
+    if args.full:
+        trace, trace_issue = trace_step(args, eng, (wav, wl, tg, tl), ar)
+        # the plans keep their steps' activations alive: release them before the sensitivity engines are built
+        plan = run = None
+        torch.cuda.empty_cache()
     if rank == 0:
         utt = world * args.batch * args.steps / elapsed
         utt_gpu = utt / world
         bf16_peak = MI355X_BF16_DENSE_TFLOPS if cfg.math == "bf16" else MI355X_F32_MFMA_TFLOPS
-
-        def rate(t):
-            n = max(1, t["launches"])
-            ms = t["ms_total"] / n
-            gbps = (t["bytes_total"] / n) / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-            tfl = (t["flops_total"] / n) / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-            return n, ms, gbps, tfl
-
-        routes = {k[5:]: v for k, v in tsum.items() if k.startswith("gemm:")}
-        # the row-parallel weight gradients run both inside kdfm_gemm (f32 operands) and as kdfm_wgrad_bf16
-        # (bf16 operands): one kernel family
-        if "wgrad_bf16" in tsum:
-            w = dict(routes.get("wgrad_rows", empty))
-            for k in ("launches", "ms_total", "flops_total", "bytes_total"):
-                w[k] = w.get(k, 0) + tsum["wgrad_bf16"][k]
-            # deferred folds (kdfm_wgrad_fold_flush: one batched launch per encoder layer) run outside the
-            # products' traced calls: their time joins the family, not their launch count (a call stays one
-            # product + its fold)
-            if "wgrad_fold" in tsum:
-                w["ms_total"] += tsum["wgrad_fold"]["ms_total"]
-            routes["wgrad_rows"] = w
-        for fam in ("ffn_fwd", "ffn_bwd", "attn_fwd", "attn_prep", "attn_bwd"):
-            if fam in tsum:
-                routes[fam] = tsum[fam]
-        by_route = {}
-        for r, t in sorted(routes.items(), key=lambda kv: -kv[1]["ms_total"]):
-            n, ms, gbps, tfl = rate(t)
-            by_route[r] = {"launches": n, "ms_per_step": round(t["ms_total"], 3), "avg_ms": round(ms, 5),
-                           "GB_per_s": round(gbps, 1), "TFLOP_per_s": round(tfl, 2),
-                           "bytes_per_launch": round(t["bytes_total"] / n, 1),
-                           "flops_per_launch": round(t["flops_total"] / n, 1),
-                           "profile_ms_per_step": profile_ms(_family_stems(r))}
-        dom = next(iter(by_route)) if by_route else "generic"
-        dt = routes.get(dom, empty)
-        n, ms, gbps, tfl = rate(dt)
-        intensity = dt["flops_total"] / max(1.0, dt["bytes_total"])
-        ridge = bf16_peak * 1e12 / (MI355X_HBM_GBPS * 1e9)
-        if intensity < ridge:
-            roof = {"bound": "hbm", "achieved": round(gbps, 1), "peak": MI355X_HBM_GBPS, "unit": "GB/s",
-                    "frac": round(gbps / MI355X_HBM_GBPS, 4)}
-        else:
-            roof = {"bound": "mfma", "achieved": round(tfl, 2), "peak": bf16_peak, "unit": "TFLOP/s",
-                    "frac": round(tfl / bf16_peak, 4)}
-        stems = FAMILY_KERNELS.get(dom) or ROUTE_KERNELS.get(dom, (dom,))
-        roof.update({"traffic": pmc_traffic(stems),
-                     "traffic_source": os.path.relpath(PMC_TRAFFIC, ROOT) + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, "
-                                       "all of the family's kernels incl. folds, per call = per main-kernel launch)",
-                     "kernel": f"{dom} family ({', '.join(stems)}): the kernel family with the largest aggregated "
-                               f"time of the step (kdfm_gemm routes + the fused kernels, HIP events on their streams)",
-                     "timing_source": trace_issue,
-                     "profile_ms_per_step": profile_ms(_family_stems(dom)),
-                     "profile_source": (os.path.relpath(_summary_path(), ROOT) + " (rocprofv3 --kernel-trace of this "
-                                        "bench command, whole steps; tools/roofline_check.py)") if _summary_path() else None,
-                     "launches": n, "avg_ms": round(ms, 5), "bytes_per_launch": round(dt["bytes_total"] / n, 1),
-                     "flops_per_launch": round(dt["flops_total"] / n, 1),
-                     "arith_intensity_flop_per_byte": round(intensity, 2)})
-        # the critical path: the compute stream carries the student chain and the whole backward's data
-        # gradients (the teacher, weight gradients and CTC/KL overlap it on their own streams)
-        csum = trace.summary(stream=eng.compute_stream.cuda_stream)
-        croutes = {k[5:]: v for k, v in csum.items() if k.startswith("gemm:")}
-        for fam in ("ffn_fwd", "ffn_bwd", "attn_fwd", "attn_prep", "attn_bwd", "wgrad_bf16"):
-            if fam in csum:
-                croutes[fam] = csum[fam]
-        crit = None
-        if croutes:
-            cdom, ct = max(croutes.items(), key=lambda kv: kv[1]["ms_total"])
-            cn, cms, cgbps, ctfl = rate(ct)
-            cint = ct["flops_total"] / max(1.0, ct["bytes_total"])
-            cb = "hbm" if cint < ridge else "mfma"
-            crit = {"bound": cb, "achieved": round(cgbps if cb == "hbm" else ctfl, 2),
-                    "peak": MI355X_HBM_GBPS if cb == "hbm" else bf16_peak, "unit": "GB/s" if cb == "hbm" else "TFLOP/s",
-                    "frac": round((cgbps / MI355X_HBM_GBPS) if cb == "hbm" else (ctfl / bf16_peak), 4),
-                    "kernel": f"{cdom} family: the most time on the compute (critical-path) stream",
-                    "ms_per_step_on_stream": round(ct["ms_total"], 3), "launches": cn, "avg_ms": round(cms, 5),
-                    "traffic": pmc_traffic(FAMILY_KERNELS.get(cdom) or ROUTE_KERNELS.get(cdom, (cdom,))),
-                    "by_family_ms": {k: round(v["ms_total"], 3) for k, v in
-                                     sorted(croutes.items(), key=lambda kv: -kv[1]["ms_total"])}}
-        # MFMA rate of the attention / FFN kernels (the north-star MFMA subject) per family
-        mfma_fams = {}
-        for fam in ("ffn_fwd", "ffn_bwd", "attn_fwd", "attn_bwd"):
-            if fam in tsum:
-                n_, ms_, _, tfl_ = rate(tsum[fam])
-                mfma_fams[fam] = {"TFLOP_per_s": round(tfl_, 2), "frac_bf16_peak": round(tfl_ / bf16_peak, 5),
-                                  "launches": n_, "avg_ms": round(ms_, 5),
-                                  "flops_per_launch": round(tsum[fam]["flops_total"] / n_, 1)}
-        fe = rate(tsum.get("frontend", empty))
-        dw = rate(tsum.get("dwconv", empty))
-        cpu = None
         _progress(f"timed {args.steps} steps: {1e3 * elapsed / args.steps:.3f} ms/step ({utt:.1f} utt/s)")
-        if not args.no_cpu_baseline and world == 1:
-            # every core this process may use: its affinity set capped by the cgroup CPU quota (the GPU
-            # box: 256 CPUs visible, cpu.max = 16 CPUs; 256 threads under that quota stall for minutes).
-            # os.cpu_count() (the whole machine) is reported beside it
-            threads = args.cpu_threads or _usable_cpus()
-            cpu = cpu_baseline(threads, args.samples)
-            cpu["cgroup_cpu_max"] = _cgroup_cpu_max()
-        f32 = v1024 = encfm = xl = xl8 = None
-        if not args.no_f32_sensitivity and cfg.math == "bf16" and world == 1:
-            _progress("f32 sensitivity")
-            f32 = sensitivity(dev, args.samples, math="f32")
-            f32["dtype"] = "f32"
-            _progress("V=1024 sensitivity")
-            v1024 = sensitivity(dev, args.samples, vocab=1024)
-            _progress("encoder-level FM + router sensitivity")
-            encfm = sensitivity(dev, args.samples, kd_model="encfm")
-            encfm["note"] = ("the asr_train.py model family on the same workload: router + flow matching on every "
-                             "hooked layer pair instead of the ver5 latent heads; not the headline value")
-            _progress("FastConformer-XL shape sensitivity")
-            xl = sensitivity(dev, args.samples, **XL_SHAPES)
-            xl["note"] = ("BASELINE.json configs[4]'s layer shapes (FastConformer-XL: d_model 1024, 8 heads, head dim "
-                          "128, 24 layers, dw_striding x8, kernel 9, no xscaling) for student and teacher on the same "
-                          "16 s x B=32 workload, bf16 (the wide Linear products on the large-tile route, "
-                          "csrc/biggemm.hip); not the headline value")
-            _progress("FastConformer-XL fp8 sensitivity")
-            xl8 = sensitivity(dev, args.samples, linear_fp8=True, **XL_SHAPES)
-            xl8["note"] = ("configs[4] at its stated precision: the same XL step with the wide Linear products' forward "
-                           "and data gradients on MX fp8 operands (e4m3 with an e8m0 scale per 32 contraction "
-                           "elements, applied by the block-scaled MFMA v_mfma_scale_f32_16x16x128_f8f6f4); attention "
-                           "core and weight gradients bf16; not the headline value")
         line = {
             "metric": "utterances/sec (FM-distill train step, Conformer-CTC-small) at 1/2/4/8 MI355X",
             "value": round(utt, 3),
@@ -574,29 +647,16 @@ def main():
                        "deterministic": cfg.deterministic,
                        "kernarg_device_memory": bool(getattr(__import__("kdfm"), "KERNARG_IN_DEVICE_MEMORY", False)),
                        "frames_subsampled": (args.samples // 160) // 4 + 1, "parallelism": f"dp{world}"},
-            "roofline": roof,
-            "roofline_by_family": by_route,
-            "roofline_critical_path": crit,
-            "mfma_attn_ffn_by_family": mfma_fams,
+            "full": args.full,
             "attn_ffn_mfma_frac": {"value": round(ATTN_FFN_GFLOP_PER_UTT * 1e9 * utt_gpu / (bf16_peak * 1e12), 5),
                                    "formula": "23.0 GFLOP/utt (SURVEY §8(d)) x utt/s per GPU / dense bf16 peak"},
             "whole_step": {"tflops": round(STEP_GFLOP_PER_UTT * 1e9 * utt_gpu / 1e12, 2),
                            "frac_bf16_peak": round(STEP_GFLOP_PER_UTT * 1e9 * utt_gpu / (bf16_peak * 1e12), 5),
                            "formula": "62.6 GFLOP/utt (SURVEY §8(d)) x utt/s per GPU"},
-            "mel_frontend_hbm": {"achieved": round(fe[2], 1), "unit": "GB/s", "peak": MI355X_HBM_GBPS,
-                                 "frac": round(fe[2] / MI355X_HBM_GBPS, 4), "launches": fe[0], "avg_ms": round(fe[1], 5),
-                                 "bytes": "4 B x (N samples + T x 80 mel) per utterance (1.54 MB at 16 s)"},
-            "dwconv_hbm": {"achieved": round(dw[2], 1), "unit": "GB/s", "peak": MI355X_HBM_GBPS,
-                           "frac": round(dw[2] / MI355X_HBM_GBPS, 4), "launches": dw[0], "avg_ms": round(dw[1], 5),
-                           "bytes": "read g + write y, 4 B x rows x d per launch"},
-            "cpu_baseline": cpu,
-            "f32_sensitivity": f32,
-            "vocab_1024_sensitivity": v1024,
-            "encoder_fm_router_sensitivity": encfm,
-            "xl_shape_sensitivity": xl,
-            "xl_fp8_sensitivity": xl8,
             "losses_last_step": [round(x, 5) for x in losses],
         }
+        if args.full:
+            line.update(full_report(args, cfg, eng, dev, world, trace, trace_issue))
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

@@ -14,11 +14,11 @@ step_tests() {
     > "$OUT/pytest_gpu.log" 2>&1
 }
 step_bench() {
-  timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 > "$OUT/bench.log" 2>&1
+  timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 > "$OUT/bench.log" 2>&1
 }
 step_prof() {
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-    -- python3 -u bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_bench.log" 2>&1
+    -- python3 -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_bench.log" 2>&1
 }
 step_tests && echo "tests ok" && step_bench && echo "bench ok" && tail -1 "$OUT/bench.log" && step_prof && echo "prof ok"
 rc=$?

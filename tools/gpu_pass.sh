@@ -8,10 +8,10 @@ OUT=gpurun_out/$T
 mkdir -p "$OUT"
 if [ "$2" = "notests" ]; then
   export TMPDIR=/tmp
-  timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
+  timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
   tail -1 "$OUT/bench.log" | cut -c1-400
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-    -- python3 -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32-sensitivity > "$OUT/prof_bench.log" 2>&1 || { echo "prof failed"; exit 4; }
+    -- python3 -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-f32-sensitivity > "$OUT/prof_bench.log" 2>&1 || { echo "prof failed"; exit 4; }
 else
   bash tools/gpu_full.sh "$T" || exit $?
 fi
