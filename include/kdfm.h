@@ -750,6 +750,38 @@ int kdfm_relpos_attn_fwd(const float* qu, const float* qv, const float* qkv, con
                          float* m_blk, int64_t B, int64_t H,
                          int64_t T, int64_t d, float scale, float dropout_p, const uint64_t* seed,
                          uint64_t rng_stream, void* stream);
+/* Limited attention context (NeMo ConformerEncoder att_context_size / att_context_style,
+ * conformer_encoder.py:107-114, _create_masks :796-850).  Query i of an utterance sees the keys
+ * [lo(i), hi(i)] intersected with its valid frames, described by three integers:
+ *   ctx_chunk == 0 ("regular"): lo = i - ctx_left (0 when ctx_left == -1), hi = i + ctx_right (T-1 when -1);
+ *   ctx_chunk  > 0 ("chunked_limited", chunk = right + 1): c = i / ctx_chunk, lo = (c - ctx_left) ctx_chunk
+ *     with ctx_left counted in CHUNKS (-1: unlimited), hi = (c + 1) ctx_chunk - 1; ctx_right is unused.
+ * Masked scores are skipped (the reference fills -10000, whose softmax weight underflows to exactly 0).
+ *   kdfm_relpos_attn_ctx_fwd: kdfm_relpos_attn_fwd's single-pass form (o and the per-row lse; same centred
+ *     keys / values and dropout index) that visits only the 64-key blocks intersecting the union of a
+ *     64-query block's windows; dk <= 128.  A window that covers every key gives kdfm_relpos_attn_fwd's bits.
+ *   kdfm_relpos_attn_ctx_bwd: the bwd2 backward (kdfm_relpos_attn_bwd2_dq / _dkv / _dpos) in one call: dqu,
+ *     dqv, dK / dV into dqkv[:, d:] / [:, 2d:], dpos (2T-1, d, overwritten).  The dQ kernel visits the same key
+ *     blocks as the forward, dK / dV walk the inverse window (the queries that see a key), dpos the in-window
+ *     band.  ds / pd: two (B, H, T, ldt) bf16 scratch buffers (ldt = kdfm_relpos_attn_bwd2_ldt(T)); only the
+ *     visited tiles are written and no other tile is read.  ws: kdfm_relpos_attn_bwd2_dpos_ws floats.
+ *     Deterministic (no atomics); the limits of the bwd2 entries apply.
+ *   kdfm_relpos_softmax_ctx_fwd: kdfm_relpos_softmax_fwd with the window (the f32 parity route): masked
+ *     probabilities are exactly 0 in P and Pdrop, so kdfm_relpos_softmax_bwd applies unchanged. */
+int kdfm_relpos_attn_ctx_fwd(const float* qu, const float* qv, const float* qkv, const float* pos,
+                             const int64_t* lengths, float* o, float* lse, int64_t B, int64_t H, int64_t T,
+                             int64_t d, float scale, float dropout_p, const uint64_t* seed, uint64_t rng_stream,
+                             int32_t ctx_left, int32_t ctx_right, int32_t ctx_chunk, void* stream);
+int kdfm_relpos_attn_ctx_bwd(const float* dO, const float* O, const float* qu, const float* qv, const float* qkv,
+                             const float* pos, const float* lse, const int64_t* lengths, uint16_t* ds, uint16_t* pd,
+                             float* dqu, float* dqv, float* dqkv, float* dpos, float* ws, int64_t ws_len, int64_t B,
+                             int64_t H, int64_t T, int64_t d, float scale, float dropout_p, const uint64_t* seed,
+                             uint64_t rng_stream, int32_t ctx_left, int32_t ctx_right, int32_t ctx_chunk,
+                             void* stream);
+int kdfm_relpos_softmax_ctx_fwd(const float* ac, const float* bd, const int64_t* lengths, float* P, float* Pdrop,
+                                int64_t B, int64_t H, int64_t T, float scale, float dropout_p, const uint64_t* seed,
+                                uint64_t rng_stream, int32_t ctx_left, int32_t ctx_right, int32_t ctx_chunk,
+                                void* stream);
 /* The same forward over PREPARED bf16 operands (csrc/attn_fwd3.hip; single pass, lse only -- the bwd2
  * backward's form -- or inference with lse NULL): the same bf16 operands, MFMAs and dropout mask as
  * kdfm_relpos_attn_fwd, its softmax in the exp2 domain (O within 1e-3, lse within 2e-6 of it).  Every operand

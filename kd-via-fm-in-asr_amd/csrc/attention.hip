@@ -5,16 +5,20 @@
 // the probabilities are re-zeroed (fully padded query rows -> all zero), then inverted dropout
 // (dropout_att) with a counter-RNG mask that the backward regenerates.
 #include "common.h"
+#include "attn_ctx.h"
 
 namespace kdfm {
 namespace {
 
 constexpr int MAXE = 8;  // T <= 512 per row (64 lanes x 8)
 
+// CTX: limited attention context (attn_ctx.h) -- keys outside the query's window are masked like padded
+// keys (probability exactly 0 in P and Pd)
+template <bool CTX>
 __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(
     const float* __restrict__ ac, const float* __restrict__ bd, const int64_t* __restrict__ lens,
     float* __restrict__ P, float* __restrict__ Pd, int64_t B, int64_t H, int T, float scale, float p_drop,
-    const uint64_t* seed_ptr, uint64_t rng_stream) {
+    const uint64_t* seed_ptr, uint64_t rng_stream, AttnCtx cx) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // (b*H + h)*T + i
   if (row >= B * H * T) return;
@@ -33,12 +37,13 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(
     }
     return;
   }
+  const int wlo = CTX ? ctx_lo(cx, i) : 0, whi = CTX ? ctx_hi(cx, i, T) : T - 1;
   float s[MAXE];
   float mx = -3.0e38f;
 #pragma unroll
   for (int e = 0; e < MAXE; ++e) {
     const int j = lane + 64 * e;
-    if (j < T && j < len) {
+    if (j < T && j < len && (!CTX || (j >= wlo && j <= whi))) {
       s[e] = (acr[j] + bdr[T - 1 - i + j]) * scale;
       mx = fmaxf(mx, s[e]);
     } else {
@@ -50,7 +55,7 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(
 #pragma unroll
   for (int e = 0; e < MAXE; ++e) {
     const int j = lane + 64 * e;
-    s[e] = (j < T && j < len) ? __expf(s[e] - mx) : 0.f;
+    s[e] = (j < T && j < len && (!CTX || (j >= wlo && j <= whi))) ? __expf(s[e] - mx) : 0.f;
     sum += s[e];
   }
   const float inv = 1.f / wave_sum(sum);
@@ -140,9 +145,27 @@ int kdfm_relpos_softmax_fwd(const float* ac, const float* bd, const int64_t* len
   KDFM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout p");
   const int64_t rows = B * H * T;
   if (rows == 0) return KDFM_OK;
-  hipLaunchKernelGGL(relpos_softmax_fwd_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, as_stream(stream),
-                     ac, bd, lengths, P, Pdrop, B, H, (int)T, scale, dropout_p, seed, rng_stream);
+  hipLaunchKernelGGL(relpos_softmax_fwd_kernel<false>, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0,
+                     as_stream(stream), ac, bd, lengths, P, Pdrop, B, H, (int)T, scale, dropout_p, seed, rng_stream,
+                     AttnCtx{-1, -1, 0});
   return check_launch("kdfm_relpos_softmax_fwd");
+}
+
+int kdfm_relpos_softmax_ctx_fwd(const float* ac, const float* bd, const int64_t* lengths, float* P, float* Pdrop,
+                                int64_t B, int64_t H, int64_t T, float scale, float dropout_p, const uint64_t* seed,
+                                uint64_t rng_stream, int32_t ctx_left, int32_t ctx_right, int32_t ctx_chunk,
+                                void* stream) {
+  using namespace kdfm;
+  KDFM_REQUIRE(ac && bd && P, "null pointer");
+  KDFM_REQUIRE(T > 0 && T <= 64 * MAXE, "T must be in (0, 512]");
+  KDFM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout p");
+  AttnCtx cx;
+  KDFM_REQUIRE(ctx_make(cx, ctx_left, ctx_right, ctx_chunk, T), "context: left / right >= -1, chunk >= 0");
+  const int64_t rows = B * H * T;
+  if (rows == 0) return KDFM_OK;
+  hipLaunchKernelGGL(relpos_softmax_fwd_kernel<true>, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0,
+                     as_stream(stream), ac, bd, lengths, P, Pdrop, B, H, (int)T, scale, dropout_p, seed, rng_stream, cx);
+  return check_launch("kdfm_relpos_softmax_ctx_fwd");
 }
 
 int kdfm_relpos_softmax_bwd(const float* P, const float* dPdrop, float* dAC, float* dBD, int64_t B, int64_t H,

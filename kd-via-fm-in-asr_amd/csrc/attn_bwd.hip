@@ -25,6 +25,7 @@
 // element is owned by one workgroup and the fold is ordered: deterministic, no atomics.
 #include "gemm_common.h"
 #include "attn_centre.h"
+#include "attn_ctx.h"
 
 // timing probe points (tools/attn_bwd_probe.hip defines KPROBE; empty in the library)
 #ifndef KPROBE
@@ -69,6 +70,7 @@ struct AbP {
   // bwd2 over prepared operands (csrc/attn_fwd3.hip): bf16 centred K / V tiles (B*H, Tp, LR), the centre
   // (B*H, 2, DKP), this layer's band rows (H, npb, LR)
   const uint16_t* kb; const uint16_t* vb; const float* cen; const uint16_t* pb; int64_t Tp, npb;
+  AttnCtx cx;   // CTX kernels: the per-query key window (attn_ctx.h)
 };
 
 constexpr uint32_t AB_OOB = 0x80000000u;   // buffer offset past every buffer: the access is dropped / reads 0
@@ -207,7 +209,10 @@ __global__ __launch_bounds__(256) void attn_rowdot_kernel(const float* __restric
 // PREP (bwd2 only): K / V / band tiles copied by LDS-DMA from the forward's prepared bf16 operands
 // (kdfm_attn_kv_prep / kdfm_attn_band_prep, the same bf16(K - kc) / bf16(V - vc) values the register path
 // stages) and the centre read from them -- no staging registers, no conversion or centring pass
-template <int NU, bool SAVE = false, bool RIN = false, bool PREP = false>
+// CTX (bwd2, register-staged): limited attention context (attn_ctx.h) -- only the key blocks that intersect the
+// union of the 64 query rows' windows are visited (and their dS / Pd tiles written, zero outside the window);
+// the other instantiations compile to the same code as before
+template <int NU, bool SAVE = false, bool RIN = false, bool PREP = false, bool CTX = false>
 __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p) {
   // the prepared tiles (PREP) pad head dims <= 48 to 48 (attn_prep_dkp): one 32-wide and one 16-wide MFMA
   // k-step over the head dim; the register-staged forms pad to 64 / 128
@@ -217,6 +222,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p
   constexpr int LRK = DKP + 8;
   static_assert(SAVE || KS == 2, "the pre-bwd2 path covers head dims <= 64 only");
   static_assert(!PREP || (SAVE && RIN), "prepared operands: the bwd2 dQ kernel only");
+  static_assert(!CTX || (SAVE && RIN && !PREP), "limited context: the register-staged bwd2 dQ kernel only");
   constexpr int KCH = BK * LRK * 2 / 1024;                  // 1 KB DMA chunks of a K / V tile
   constexpr int PCH = (PB1 * LRK * 2 + 1023) / 1024;        // ... of the band (rows past 143 unused)
   static_assert(BK * LRK * 2 % 1024 == 0, "K / V tiles must be whole 1 KB chunks");
@@ -239,6 +245,9 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p
   const int i0 = (int)blk.x * BQ;
   const int len = p.lens ? (int)min<int64_t>(p.lens[b], p.T) : T;
   const int nkb = (len + BK - 1) / BK;
+  // the key blocks [kb0, kb1) this workgroup visits
+  const int kb0 = CTX ? ctx_lo(p.cx, i0) / BK : 0;
+  const int kb1 = CTX ? min(nkb, ctx_hi(p.cx, min(i0 + BQ - 1, T - 1), T) / BK + 1) : nkb;
   const int npos = 2 * T - 1;
   const int64_t hoff = h * p.dkh;
   if constexpr (PREP) {
@@ -286,6 +295,10 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p
     rs[r] = (ok && !RIN) ? p.rsum[bh * p.T + ib + r] : 0.f;
     ls[r] = ok ? p.lse[bh * p.T + ib + r] : 3.0e38f;
   }
+  uint32_t win[4];   // CTX: the owned rows' windows, lo | hi << 16 (T <= 4096; one register per row)
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    win[r] = CTX ? (uint32_t)ctx_lo(p.cx, ib + r) | ((uint32_t)ctx_hi(p.cx, ib + r, T) << 16) : 0u;
 
   // bwd2 (SAVE): the forward's softmax in the exp2 domain (P = exp2(s_raw scale log2e - lse log2e)), S_bd by lane
   // permutes of the G accumulators (attn_fwd3.hip: S_bd(t, r) = G[t + (off >= 16)][r] of lane (off & 15) + 16 q4),
@@ -353,7 +366,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p
     }
   };
   if constexpr (SAVE) {   // the first block's loads in flight behind the centre and row-sum prologue
-    if (nkb > 0) fetch(0);
+    if (kb0 < kb1) fetch(kb0);
   }
 
   // the forward's centring (attn_centre.h): K rows staged as K_j - kc (the scores, hence P = exp(s - lse),
@@ -429,7 +442,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p
   const __amdgpu_buffer_rsrc_t rpd = __builtin_amdgcn_make_buffer_rsrc((void*)p.pdo, (short)0, sbytes, 0x00020000);
   if (!SAVE && nkb > 0) fetch(0);
   KPROBE(1);
-  for (int kb = 0; kb < nkb; ++kb) {
+  for (int kb = kb0; kb < kb1; ++kb) {
     const int j0 = kb * BK;
     if constexpr (PREP) {
       if (kb > 0) {
@@ -446,7 +459,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p
       put_rows<NU, LRK>(Ks, nullptr, 0, nk, BK, dk);
       put_rows<2 * NU, LRK>(Pr, nullptr, 0, nb, 127, dk);
       __syncthreads();
-      if (kb + 1 < nkb) fetch(kb + 1);
+      if (kb + 1 < kb1) fetch(kb + 1);
     }
     KPROBE(2 + 4 * kb);
     // ---- S of this wave's 16 rows x 64 keys: the forward's scores (relpos_attn_fwd_kernel) ----
@@ -554,7 +567,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dq_kernel(AbP p
         float dsv[4], pdv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const bool ok = ib + r < len && j < len;
+          const bool ok = ib + r < len && j < len && (!CTX || (j >= (int)(win[r] & 0xffffu) && j <= (int)(win[r] >> 16)));
           float g = a[t][r] + cs[r];
           bool kp = true;
           if (p.p_drop > 0.f) {
@@ -963,8 +976,10 @@ __global__ __launch_bounds__(256) void attn_dpos_fold_kernel(const float* __rest
 // one workgroup per (b, h, 64 keys), 4 waves x 16 keys; per 64-query block the dO / Qu rows are staged
 // [query][c] and the Pd / dS tiles [query][key] as copied (16-byte loads of 128-byte row runs), all four
 // read TRANSPOSED into MFMA fragments (ds_read_b64_tr_b16).  No recompute of P, dP or the dropout mask.
+// CTX: the inverse window -- only the query blocks with a row that sees one of these 64 keys (exactly the
+// (query block, key block) tiles the CTX dQ kernel wrote; the rest of dS / Pd is never read).
 // ---------------------------------------------------------------------------------------------
-template <int NU>
+template <int NU, bool CTX = false>
 __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dkv2_kernel(AbP p) {
   constexpr int LRK = 32 * (NU > 4 ? 4 : 2) + 8;   // row stride of the [query][c] images (head dim padded)
   __shared__ __attribute__((aligned(16))) uint16_t Os[BQ * LRK];     // dO block [query][c]
@@ -989,6 +1004,9 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dkv2_kernel(AbP
 #pragma unroll
   for (int u = 0; u < NU; ++u) { adv[u] = f32x4{0.f, 0.f, 0.f, 0.f}; adk[u] = adv[u]; }
   const int nqb = (j0 < len) ? (len + BQ - 1) / BQ : 0;
+  // the query blocks [qb0, qb1) this workgroup visits
+  const int qb0 = CTX ? ctx_qlo(p.cx, j0) / BQ : 0;
+  const int qb1 = CTX ? min(nqb, ctx_qhi(p.cx, min(j0 + BK - 1, T - 1), T) / BQ + 1) : nqb;
   typedef __attribute__((ext_vector_type(4))) uint32_t u32x4v;
   float4 ndo[NU], nqu[NU];
   u32x4v npd[2], nds[2];
@@ -1007,8 +1025,8 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dkv2_kernel(AbP
       nds[q] = __builtin_amdgcn_raw_buffer_load_b128(rds, off, 0, 0);
     }
   };
-  if (nqb > 0) fetch(0);
-  for (int qb = 0; qb < nqb; ++qb) {
+  if (qb0 < qb1) fetch(qb0);
+  for (int qb = qb0; qb < qb1; ++qb) {
     __syncthreads();
     put_rows<NU, LRK>(Os, nullptr, 0, ndo, BQ, dk);
     put_rows<NU, LRK>(Qs, nullptr, 0, nqu, BQ, dk);
@@ -1019,7 +1037,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dkv2_kernel(AbP
       *reinterpret_cast<u32x4v*>(Dq + row * LW + 8 * c8) = nds[q];
     }
     __syncthreads();
-    if (qb + 1 < nqb) fetch(qb + 1);
+    if (qb + 1 < qb1) fetch(qb + 1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const bf16x8 pa = tr_frag(Pq, LW, ks * 32, 16 * w, lane);   // A[key][q] = Pd[q][key]
@@ -1049,8 +1067,10 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dkv2_kernel(AbP
 // bwd2 kernel 3b: per-chunk partials of dPpos[r] = sum_{b, i} dS[i][r - (T-1) + i] Qv_i over the saved bf16
 // dS: per (h, 64 positions, batch chunk), query steps of 32 rows; the dS band [32][96] of the step is
 // staged from HBM, the skewed A fragments and Qv^T read as kernel 3 does.
+// CTX: steps whose (32 queries, 96 keys) band misses every window are skipped and only in-window elements
+// are read (all inside tiles the CTX dQ kernel wrote).
 // ---------------------------------------------------------------------------------------------
-template <int NU>
+template <int NU, bool CTX = false>
 __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dpos2_kernel(AbP p) {
   __shared__ __attribute__((aligned(16))) uint16_t Dl[NPQ * LDL];    // dS [i - ib0][j - jbase]
   constexpr int DKP = 32 * (NU > 4 ? 4 : 2);
@@ -1071,20 +1091,23 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dpos2_kernel(Ab
   const int64_t b0 = bchunk * p.bpc;
   const int64_t b1 = min<int64_t>(p.B, b0 + p.bpc);
   auto ulen = [&](int64_t bb) { return p.lens ? (int)min<int64_t>(p.lens[bb], p.T) : T; };
+  // the step (queries ib.., keys jb..) addresses a valid key (CTX: inside some row's window)
+  auto hits = [&](int ib, int jb, int ln) -> bool {
+    if (jb + NPJ <= 0 || jb >= ln) return false;
+    if constexpr (CTX) {
+      if (ctx_lo(p.cx, ib) > jb + NPJ - 1 || ctx_hi(p.cx, min(ib + NPQ - 1, T - 1), T) < jb) return false;
+    }
+    return true;
+  };
   auto advance = [&](int64_t& bb, int& ib, int& ln) -> bool {
     ib += NPQ;
     while (bb < b1) {
-      for (; ib < ln; ib += NPQ) {
-        const int jb = r0 - (T - 1) + ib;
-        if (!(jb + NPJ <= 0 || jb >= ln)) return true;
-      }
+      for (; ib < ln; ib += NPQ)
+        if (hits(ib, r0 - (T - 1) + ib, ln)) return true;
       if (++bb >= b1) break;
       ib = 0;
       ln = ulen(bb);
-      if (ib < ln) {
-        const int jb = r0 - (T - 1) + ib;
-        if (!(jb + NPJ <= 0 || jb >= ln)) return true;
-      }
+      if (ib < ln && hits(ib, r0 - (T - 1) + ib, ln)) return true;
     }
     return false;
   };
@@ -1100,7 +1123,8 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void attn_bwd_dpos2_kernel(Ab
       const int e = threadIdx.x + 256 * it;
       const int il = e / NPJ, jl = e - il * NPJ;
       const int i = ib + il, j = jb + jl;
-      nd[it] = (i < ln && j >= 0 && j < ln) ? p.ds[(bhh * p.T + i) * p.ldt + j] : (uint16_t)0;
+      const bool vis = !CTX || (j >= ctx_lo(p.cx, i) && j <= ctx_hi(p.cx, i, T));
+      nd[it] = (i < ln && j >= 0 && j < ln && vis) ? p.ds[(bhh * p.T + i) * p.ldt + j] : (uint16_t)0;
     }
   };
   int64_t b = b0;
@@ -1356,6 +1380,63 @@ int kdfm_relpos_attn_bwd2_dpos(const float* qv, const uint16_t* ds, const int64_
   hipLaunchKernelGGL(attn_dpos_fold_kernel, dim3((unsigned)ceil_div(npos * d, 256)), dim3(256), 0, st, p.dpos_part,
                      dpos, npos * d, chunks);
   return check_launch("kdfm_relpos_attn_bwd2_dpos(fold)");
+}
+
+// bwd2 with a limited attention context (the (left, right, chunk) triple of attn_ctx.h; the forward is
+// kdfm_relpos_attn_ctx_fwd): the dQ kernel over the visited key blocks, then dK / dV over the inverse window
+// and dPpos over the in-window band, in that order on `stream`.  ds / pd: (B, H, T, ldt) bf16 scratch -- only
+// the visited (query block, key block) tiles are written and only those are read.
+int kdfm_relpos_attn_ctx_bwd(const float* dO, const float* O, const float* qu, const float* qv, const float* qkv,
+                             const float* pos, const float* lse, const int64_t* lengths, uint16_t* ds, uint16_t* pd,
+                             float* dqu, float* dqv, float* dqkv, float* dpos, float* ws, int64_t ws_len, int64_t B,
+                             int64_t H, int64_t T, int64_t d, float scale, float dropout_p, const uint64_t* seed,
+                             uint64_t rng_stream, int32_t ctx_left, int32_t ctx_right, int32_t ctx_chunk,
+                             void* stream) {
+  using namespace kdfm;
+  KDFM_REQUIRE(dO && O && qu && qv && qkv && pos && lse && ds && pd && dqu && dqv && dqkv && dpos && ws, "null pointer");
+  KDFM_REQUIRE((((uintptr_t)dO | (uintptr_t)O | (uintptr_t)qu | (uintptr_t)qv | (uintptr_t)qkv | (uintptr_t)pos |
+                 (uintptr_t)ds | (uintptr_t)pd) & 15) == 0, "operands must be 16-byte aligned");
+  KDFM_REQUIRE(B * T * 3 * d * 4 < (1ll << 31), "qkv larger than 2 GiB (buffer offsets)");
+  KDFM_REQUIRE(ws_len >= kdfm_relpos_attn_bwd2_dpos_ws(B, T, d), "workspace too small (kdfm_relpos_attn_bwd2_dpos_ws)");
+  AttnCtx cx;
+  KDFM_REQUIRE(ctx_make(cx, ctx_left, ctx_right, ctx_chunk, T), "context: left / right >= -1, chunk >= 0");
+  AbP p;
+  int rc = ab2_setup(p, qu, qv, qkv, lse, lengths, B, H, T, d, scale, dropout_p, seed, rng_stream);
+  if (rc || B == 0) return rc;
+  p.dO = dO; p.pos = pos; p.dqu = dqu; p.dqv = dqv; p.ds = ds; p.pdo = pd; p.O = O;
+  p.dk = dqkv + d; p.dv = dqkv + 2 * d; p.dpos_part = ws; p.cx = cx;
+  hipStream_t st = as_stream(stream);
+  const dim3 gq((unsigned)ceil_div(T, BQ), (unsigned)(B * H)), gk((unsigned)ceil_div(T, BK), (unsigned)(B * H));
+  const int chunks = (int)(B < DPOS_MAX_CHUNKS ? B : DPOS_MAX_CHUNKS);
+  const int64_t npos = 2 * T - 1;
+  const dim3 gp((unsigned)ceil_div(npos, 64), (unsigned)H, (unsigned)chunks);
+  if (p.dkh > 64)
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<8, true, true, false, true>), gq, dim3(256), 0, st, p);
+  else if (p.dkh > 48)
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<4, true, true, false, true>), gq, dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<3, true, true, false, true>), gq, dim3(256), 0, st, p);
+  rc = check_launch("kdfm_relpos_attn_ctx_bwd(dq)");
+  if (rc) return rc;
+  if (p.dkh > 64)
+    hipLaunchKernelGGL((attn_bwd_dkv2_kernel<8, true>), gk, dim3(256), 0, st, p);
+  else if (p.dkh > 48)
+    hipLaunchKernelGGL((attn_bwd_dkv2_kernel<4, true>), gk, dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((attn_bwd_dkv2_kernel<3, true>), gk, dim3(256), 0, st, p);
+  rc = check_launch("kdfm_relpos_attn_ctx_bwd(dkv)");
+  if (rc) return rc;
+  if (p.dkh > 64)
+    hipLaunchKernelGGL((attn_bwd_dpos2_kernel<8, true>), gp, dim3(256), 0, st, p);
+  else if (p.dkh > 48)
+    hipLaunchKernelGGL((attn_bwd_dpos2_kernel<4, true>), gp, dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((attn_bwd_dpos2_kernel<3, true>), gp, dim3(256), 0, st, p);
+  rc = check_launch("kdfm_relpos_attn_ctx_bwd(dpos)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(attn_dpos_fold_kernel, dim3((unsigned)ceil_div(npos * d, 256)), dim3(256), 0, st, p.dpos_part,
+                     dpos, npos * d, chunks);
+  return check_launch("kdfm_relpos_attn_ctx_bwd(fold)");
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 // Output O is written straight into the (rows, d) head-interleaved layout.
 #include "gemm_common.h"
 #include "attn_centre.h"
+#include "attn_ctx.h"
 
 // timing probe points (tools/attn_probe.hip defines KPROBE; empty in the library)
 #ifndef KPROBE
@@ -44,6 +45,7 @@ struct AttnP {
   int64_t B, H, T, d, dk, ldq, ldkv;
   float scale, p_drop;
   const uint64_t* seed; uint64_t rng_stream;
+  AttnCtx cx;   // CTX kernels: the per-query key window (attn_ctx.h)
 };
 
 __device__ __forceinline__ bf16x8 load_frag8(const float* head, int c0, int valid) {
@@ -94,12 +96,16 @@ __device__ __forceinline__ float group16_sum(float v) {
 // 1024 / 8 heads); the head dim is padded to KS MFMA k-steps of 32 (2, or 4 for NU = 8); WPT (single pass): p~ and m_blk
 // are written -- through buffer stores whose out-of-range lanes carry an offset past the buffer (dropped
 // by the range check) instead of a branch, so each key block issues a fixed number of stores and the
-// wait for the next block's staged loads counts past them instead of draining them (vmcnt(0))
-template <bool TWO_PASS, int NU, bool WPT = false>
+// wait for the next block's staged loads counts past them instead of draining them (vmcnt(0)).
+// CTX (single pass, lse only): limited attention context (attn_ctx.h) -- the workgroup walks only the key
+// blocks that intersect the union of its 64 query rows' windows and masks inside them; the full-context
+// instantiations compile to the same code as before (the block range is [0, nkb), no window test)
+template <bool TWO_PASS, int NU, bool WPT = false, bool CTX = false>
 __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void relpos_attn_fwd_kernel(AttnP p) {
   constexpr int KS = NU > 4 ? 4 : 2;   // MFMA k-steps over the padded head dim
   constexpr int DKP = 32 * KS;         // head dim padded
   constexpr int LDR = DKP + 8;         // bf16 row stride of the [row][c] tiles (K, P band)
+  static_assert(!CTX || (!TWO_PASS && !WPT), "limited context: the single-pass lse-only form");
   __shared__ __attribute__((aligned(16))) uint16_t Ks[AKB * LDR];
   __shared__ __attribute__((aligned(16))) uint16_t Vt[DKP * LDVT];
   __shared__ __attribute__((aligned(16))) uint16_t Pr[BAND * LDR];
@@ -116,6 +122,9 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void relpos_attn_fwd_kernel(A
   const int i0 = (int)blk.x * AQ;
   const int len = p.lens ? (int)p.lens[b] : T;
   const int nkb = (min(len, T) + AKB - 1) / AKB;  // key blocks with at least one valid key
+  // single pass: the key blocks [kb0, kb1) this workgroup visits
+  const int kb0 = CTX ? ctx_lo(p.cx, i0) / AKB : 0;
+  const int kb1 = CTX ? min(nkb, ctx_hi(p.cx, min(i0 + AQ - 1, T - 1), T) / AKB + 1) : nkb;
   const int npos = 2 * T - 1;
   constexpr uint32_t OOB = 0x80000000u;
   const int nkb_all = (T + AKB - 1) / AKB;
@@ -149,6 +158,12 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void relpos_attn_fwd_kernel(A
   float mrow[4], lrow[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { mrow[r] = -3.0e38f; lrow[r] = 0.f; }
+  int wlo[4], whi[4];   // CTX: the owned rows' windows
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    wlo[r] = CTX ? ctx_lo(p.cx, ib + r) : 0;
+    whi[r] = CTX ? ctx_hi(p.cx, ib + r, T) : 0;
+  }
 
   // ---- staging of one key block: all global loads of a stage are issued before any LDS store
   // (register staging; the next block's loads are in flight while this block computes).  The per-thread
@@ -267,7 +282,8 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void relpos_attn_fwd_kernel(A
         const int ii = 4 * (lane >> 4) + r, jj = 16 * t + (lane & 15);
         const int j = j0 + jj;
         const float bd = G[ii * LDG + jj - ii + 15];
-        s[t][r] = (j < len && j < T) ? (ac[t][r] + bd) * p.scale : -3.0e38f;
+        const bool vis = !CTX || (j >= wlo[r] && j <= whi[r]);
+        s[t][r] = (j < len && j < T && vis) ? (ac[t][r] + bd) * p.scale : -3.0e38f;
       }
     wave_lds_sync();  // G is rewritten by the next call
   };
@@ -275,7 +291,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void relpos_attn_fwd_kernel(A
   // ---- pass 1 (two-pass mode): row max / sum ----
   // (the first stage's loads are issued before the centre: they are raw rows, centred at store time)
   if (TWO_PASS && nkb > 0) load_stage(0, false);
-  if (!TWO_PASS && nkb > 0) load_stage(0, true);
+  if (!TWO_PASS && kb0 < kb1) load_stage(kb0 * AKB, true);
   kv_centre<DKP>(kbase, vbase, p.ldkv, min(len, T), dk, Cn);
   if constexpr (WPT) {
     // the loop body leaves its 4 m_blk + 16 p~ stores behind the next block's loads; the same number of
@@ -334,7 +350,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void relpos_attn_fwd_kernel(A
   // single pass: only the key blocks with a valid key (the p~ zeros of the first block past them are
   // written after the loop), and the next stage is always loaded (the last block reloads itself), so
   // every iteration issues the same loads and stores
-  for (int kb = 0; kb < (TWO_PASS ? nkb_all : nkb); ++kb) {
+  for (int kb = (TWO_PASS ? 0 : kb0); kb < (TWO_PASS ? nkb_all : kb1); ++kb) {
     const int j0 = kb * AKB;
     const bool live = TWO_PASS ? kb < nkb : true;
     if (live) {
@@ -344,7 +360,7 @@ __global__ __launch_bounds__(256, NU == 3 ? 2 : 1) void relpos_attn_fwd_kernel(A
       if (TWO_PASS) {
         if (kb + 1 < nkb) load_stage(j0 + AKB, true);
       } else {
-        load_stage(kb + 1 < nkb ? j0 + AKB : j0, true);
+        load_stage(kb + 1 < kb1 ? j0 + AKB : j0, true);
       }
     }
     KPROBE(2 + 4 * kb);
@@ -496,6 +512,7 @@ extern "C" int kdfm_relpos_attn_fwd(const float* qu, const float* qv, const floa
   p.o = o; p.P = P; p.Pd = Pdrop; p.lse = lse; p.pt = p_tilde; p.mblk = m_blk;
   p.B = B; p.H = H; p.T = T; p.d = d; p.dk = dk; p.ldq = d; p.ldkv = 3 * d;
   p.scale = scale; p.p_drop = dropout_p; p.seed = seed; p.rng_stream = rng_stream;
+  p.cx = AttnCtx{-1, -1, 0};
   dim3 grid((unsigned)ceil_div(T, AQ), (unsigned)(B * H));
   const bool two = P || Pdrop, wide = dk > 48;
   KDFM_REQUIRE(!p_tilde || B * H * T * T * 2 <= (int64_t)INT32_MAX, "p~ exceeds the 2 GB buffer-offset range");
@@ -514,4 +531,37 @@ extern "C" int kdfm_relpos_attn_fwd(const float* qu, const float* qv, const floa
   else
     hipLaunchKernelGGL((relpos_attn_fwd_kernel<false, 4>), grid, dim3(256), 0, as_stream(stream), p);
   return check_launch("kdfm_relpos_attn_fwd");
+}
+
+// The single-pass forward with a limited attention context (NeMo att_context_size / att_context_style as
+// the (left, right, chunk) triple of attn_ctx.h): same operands, centring, dropout index and outputs as
+// kdfm_relpos_attn_fwd's lse-only form; key blocks outside a query block's window are not visited.
+extern "C" int kdfm_relpos_attn_ctx_fwd(const float* qu, const float* qv, const float* qkv, const float* pos,
+                                        const int64_t* lengths, float* o, float* lse, int64_t B, int64_t H, int64_t T,
+                                        int64_t d, float scale, float dropout_p, const uint64_t* seed,
+                                        uint64_t rng_stream, int32_t ctx_left, int32_t ctx_right, int32_t ctx_chunk,
+                                        void* stream) {
+  using namespace kdfm;
+  KDFM_REQUIRE(qu && qv && qkv && pos && o, "null pointer");
+  KDFM_REQUIRE(H > 0 && d % H == 0, "d must be a multiple of H");
+  const int64_t dk = d / H;
+  KDFM_REQUIRE(dk <= 128 && dk % 4 == 0, "head dim must be a multiple of 4 and <= 128");
+  KDFM_REQUIRE(T > 0 && T <= 4096, "T out of range");
+  KDFM_REQUIRE(d % 4 == 0, "d must be a multiple of 4");
+  KDFM_REQUIRE(dropout_p == 0.f || seed, "dropout needs a seed");
+  AttnP p;
+  KDFM_REQUIRE(ctx_make(p.cx, ctx_left, ctx_right, ctx_chunk, T), "context: left / right >= -1, chunk >= 0");
+  if (B == 0) return KDFM_OK;
+  p.qu = qu; p.qv = qv; p.k = qkv + d; p.v = qkv + 2 * d; p.pos = pos; p.lens = lengths;
+  p.o = o; p.P = nullptr; p.Pd = nullptr; p.lse = lse; p.pt = nullptr; p.mblk = nullptr;
+  p.B = B; p.H = H; p.T = T; p.d = d; p.dk = dk; p.ldq = d; p.ldkv = 3 * d;
+  p.scale = scale; p.p_drop = dropout_p; p.seed = seed; p.rng_stream = rng_stream;
+  dim3 grid((unsigned)ceil_div(T, AQ), (unsigned)(B * H));
+  if (dk > 64)
+    hipLaunchKernelGGL((relpos_attn_fwd_kernel<false, 8, false, true>), grid, dim3(256), 0, as_stream(stream), p);
+  else if (dk > 48)
+    hipLaunchKernelGGL((relpos_attn_fwd_kernel<false, 4, false, true>), grid, dim3(256), 0, as_stream(stream), p);
+  else
+    hipLaunchKernelGGL((relpos_attn_fwd_kernel<false, 3, false, true>), grid, dim3(256), 0, as_stream(stream), p);
+  return check_launch("kdfm_relpos_attn_ctx_fwd");
 }

@@ -89,6 +89,11 @@ class Ver5Config:
     subsampling_conv_channels: int = -1   # -1: d_model
     causal_downsampling: bool = False
     xscaling: bool = True                 # x * sqrt(d_model) after subsampling (RelPositionalEncoding)
+    # limited attention context of the STUDENT encoder (conformer_encoder.py:107-114, _create_masks :796-850):
+    # (left, right) in frames after subsampling, -1 = unlimited; style "regular" or "chunked_limited"
+    # (att_context_triple validates them).  The frozen teacher stays full-context.
+    att_context_size: tuple = (-1, -1)
+    att_context_style: str = "regular"
     bn_momentum: float = 0.1
     ln_eps: float = 1e-5
     bn_eps: float = 1e-5
@@ -138,6 +143,39 @@ def sub_stages(cfg: Ver5Config) -> int:
     elif cfg.subsampling != "dw_striding":
         raise ValueError(f"subsampling {cfg.subsampling!r} is not on this path (striding | dw_striding)")
     return f.bit_length() - 1
+
+
+FULL_CONTEXT = (-1, -1, 0)
+
+
+def att_context_triple(size=(-1, -1), style: str = "regular") -> tuple:
+    """NeMo's (att_context_size, att_context_style) -> the kernels' (left, right, chunk) triple
+    (include/kdfm.h, kdfm_relpos_attn_ctx_fwd): chunk 0 = "regular" (query i sees [i - left, i + right], -1
+    unlimited); chunk > 0 = "chunked_limited" with right >= 0 (chunk = right + 1, left counted in chunks, right
+    unused); "chunked_limited" with right == -1 is regular (left, -1).  ValueError for the reference's invalid
+    combinations (conformer_encoder.py:860-880)."""
+    try:
+        left, right = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"att_context_size must be a (left, right) pair of ints, got {size!r}") from None
+    if left < -1 or right < -1:
+        raise ValueError(f"att_context_size {size!r}: a negative context other than -1 (unlimited) is invalid")
+    if style == "regular":
+        return (left, right, 0)
+    if style != "chunked_limited":
+        raise ValueError(f"att_context_style must be 'regular' or 'chunked_limited', got {style!r}")
+    if right == -1:
+        return (left, -1, 0)
+    chunk = right + 1
+    if left >= 0 and left % chunk != 0:
+        raise ValueError(f"att_context_size {size!r}: with chunked_limited the left context must be a multiple "
+                         f"of right + 1 = {chunk}")
+    return (left // chunk if left >= 0 else -1, right, chunk)
+
+
+def att_context(cfg: Ver5Config) -> tuple:
+    """The kernel triple of cfg's att_context_size / att_context_style."""
+    return att_context_triple(cfg.att_context_size, cfg.att_context_style)
 
 
 def sub_pad(cfg: Ver5Config) -> tuple:
@@ -434,6 +472,6 @@ def fused_groups(specs: list) -> dict:
 DEFAULT = Ver5Config()
 PARITY = DEFAULT.parity()
 
-__all__ = ["Ver5Config", "DEFAULT", "PARITY", "encoder_specs", "subsampling_specs", "sub_stages", "sub_pad",
+__all__ = ["Ver5Config", "DEFAULT", "PARITY", "FULL_CONTEXT", "att_context_triple", "att_context", "encoder_specs", "subsampling_specs", "sub_stages", "sub_pad",
            "sub_channels", "sub_len", "sub_dims", "decoder_specs", "head_specs", "all_head_specs", "diffkd_specs", "encfm_specs", "meta_specs", "meta_bn_specs", "encfm_fixed_steps", "head_modules", "student_specs",
            "teacher_specs", "bn_buffer_specs", "fused_groups", "field"]

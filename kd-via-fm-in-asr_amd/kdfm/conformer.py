@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from . import kernels as K
 from .overlap import WGRAD
-from .config import Ver5Config, sub_channels, sub_dims, sub_pad, sub_stages
+from .config import Ver5Config, att_context, sub_channels, sub_dims, sub_pad, sub_stages
 
 # dropout site ids (rng stream = model_salt * 4096 + layer * 16 + site)
 SITE_FF1_ACT, SITE_FF1_OUT, SITE_ATT_P, SITE_ATT_OUT, SITE_CONV_OUT, SITE_FF2_ACT, SITE_FF2_OUT = range(7)
@@ -70,8 +70,11 @@ def _stream(salt, layer, site):
 
 
 class EncoderShapes:
-    def __init__(self, cfg: Ver5Config, B: int, T_mel: int, d: int, h: int):
+    def __init__(self, cfg: Ver5Config, B: int, T_mel: int, d: int, h: int, ctx=None):
+        """ctx: the encoder's attention-context triple (config.att_context_triple); None: cfg's (the engine's
+        frozen teacher passes FULL_CONTEXT)."""
         self.B, self.Tm, self.d, self.h = B, T_mel, d, h
+        self._ctx = att_context(cfg) if ctx is None else tuple(ctx)
         self.dk = d // h
         self.C = sub_channels(cfg, d)
         self.stages = sub_dims(cfg, T_mel)      # [(T, F)] of the subsampling input and stage outputs
@@ -80,6 +83,18 @@ class EncoderShapes:
         self.T, self.F2 = self.stages[-1]       # F2: features per frame at the subsampling output
         self.rows = B * self.T
         self.ff = cfg.ff_expansion * d
+
+    @property
+    def ctx(self):
+        """The limited attention context (left, right, chunk) of this encoder at T frames, or None when every
+        query sees every key (the default, and any window that covers the sequence): the full-context path."""
+        left, right, chunk = self._ctx
+        T = self.T
+        if chunk > 0:
+            full = chunk >= T
+        else:
+            full = (left < 0 or left >= T - 1) and (right < 0 or right >= T - 1)
+        return None if full else self._ctx
 
 
 def compute_lengths(cfg: Ver5Config, wav_len, mel_len, len1, len2, hop):
@@ -501,6 +516,12 @@ def _ln_bf16(rows, d, n, save):
         not save or _big_all((n, d, rows, _lib.BIG_TN)))
 
 
+def _attn_ctx_ok(dk, save):
+    """A limited attention context runs on the windowed fused kernels (bf16, single pass, bwd2 backward);
+    otherwise (f32 math, or the fused backward switched off) on the unfused chain over relpos_softmax_ctx_fwd."""
+    return _attn_fused_ok(dk, save) and (not save or (_ATTN_BWD_FUSED and _ATTN_BWD2))
+
+
 def _fwd3_ok(dk, save):
     """The prepared-operand attention forward applies (bf16 fused attention, single pass)."""
     return _ATTN_FWD3 and _attn_fused_ok(dk, save) and (not save or (_ATTN_BWD_FUSED and _ATTN_BWD2))
@@ -550,7 +571,15 @@ def layer_forward(cfg, S: EncoderShapes, P, L, li, x, out, pos_emb, lengths, *, 
         ppos = _empty(npos, d, dev=dev)
         K.linear(pos_emb, P[L + "self_attn.linear_pos.weight"], None, ppos)
     o = _empty(rows, d, dev=dev)
-    if _fwd3_ok(dk, save):
+    actx = S.ctx
+    if actx is not None and _attn_ctx_ok(dk, save):
+        # limited attention context: the register-staged single pass over the key blocks inside the window
+        # (csrc/attn_fused.hip CTX); lse for the windowed bwd2 backward when training
+        Pm = Pd = pt = mblk = None
+        lse = torch.empty(B, H, T, device=dev) if save else None
+        K.relpos_attn_ctx_fwd(qu, qv, qkv, ppos, lengths, o, B, H, T, 1.0 / math.sqrt(dk), pa, seed,
+                              _stream(salt, li, SITE_ATT_P), actx, lse=lse)
+    elif actx is None and _fwd3_ok(dk, save):
         # prepared operands: bf16 centred K / V tiles of this layer, the encoder's band rows (pband, or this
         # layer's own); lse for the bwd2 backward when training
         Pm = Pd = pt = mblk = None
@@ -563,7 +592,7 @@ def layer_forward(cfg, S: EncoderShapes, P, L, li, x, out, pos_emb, lengths, *, 
         if save and _ATTN_DQ3:
             keep(attn_prep=prep, attn_pband=pband)
         del prep
-    elif _attn_fused_ok(dk, save):
+    elif actx is None and _attn_fused_ok(dk, save):
         # fused flash-style kernel: no AC / BD materialisation; P (and P_drop) only when the
         # backward needs them
         if _ATTN_BWD_FUSED:
@@ -591,8 +620,12 @@ def layer_forward(cfg, S: EncoderShapes, P, L, li, x, out, pos_emb, lengths, *, 
                batch=(B, H), bA=(T * d, dk), bB=(0, dk), bC=(H * T * npos, T * npos))
         Pm = _empty(B, H, T, T, dev=dev)
         Pd = _empty(B, H, T, T, dev=dev) if pa > 0 else Pm
-        K.relpos_softmax_fwd(ac, bd, lengths, Pm, Pd if pa > 0 else None, B, H, T, 1.0 / math.sqrt(dk), pa, seed,
-                             _stream(salt, li, SITE_ATT_P))
+        if actx is not None:
+            K.relpos_softmax_ctx_fwd(ac, bd, lengths, Pm, Pd if pa > 0 else None, B, H, T, 1.0 / math.sqrt(dk), pa,
+                                     seed, _stream(salt, li, SITE_ATT_P), actx)
+        else:
+            K.relpos_softmax_fwd(ac, bd, lengths, Pm, Pd if pa > 0 else None, B, H, T, 1.0 / math.sqrt(dk), pa, seed,
+                                 _stream(salt, li, SITE_ATT_P))
         del ac, bd
         # O = Pd V : A = Pd (T x T), B(j,c) = V[b,j,h*dk+c]  -> o[b,i,h*dk+c]
         K.gemm(Pd, qkv[:, 2 * d:], o, T, dk, T, T, 1, 3 * d, 1, d, 1, amode=_lib.LD_KC, bmode=_lib.LD_XC,
@@ -617,10 +650,10 @@ def layer_forward(cfg, S: EncoderShapes, P, L, li, x, out, pos_emb, lengths, *, 
         K.linear(o_in, P[L + "self_attn.linear_out.weight"], P[L + "self_attn.linear_out.bias"], x2, epi=_lib.EPI_RESID,
                  R=x1, rscale=1.0, dropout_p=pd, seed=seed, rng_stream=_stream(salt, li, SITE_ATT_OUT))
         del o_in
-    fused_attn = _attn_fused_ok(dk, save) and _ATTN_BWD_FUSED
+    fused_attn = (_attn_fused_ok(dk, save) and _ATTN_BWD_FUSED) if actx is None else _attn_ctx_ok(dk, save)
     keep(x1=x1, ln2=ln2, m2=m2, r2=r2, qkv=qkv, qu=qu, qv=qv, ppos=ppos, P=Pm, Pd=Pd, o=o, o_h=o_h, pa=pa,
          attn_fused=fused_attn, lse=lse if fused_attn else None, pt=pt if fused_attn else None,
-         mblk=mblk if fused_attn else None)
+         mblk=mblk if fused_attn else None, attn_ctx=actx if fused_attn else None)
     del ln2, qkv, qu, qv, ppos, Pm, Pd, o
 
     # ---- convolution module ----
@@ -909,6 +942,12 @@ def layer_backward(cfg, S: EncoderShapes, P, G, L, li, ctx, dout, pos_emb, lengt
         # the positional-term gradient dPpos feeds only the linear_pos weight gradient: it runs on the
         # weight-gradient stream beside the dQ / dK,dV kernels the main stream needs next
         lse, pt, mblk = ctx["lse"], ctx["pt"], ctx["mblk"]
+        if ctx.get("attn_ctx") is not None:   # limited attention context: the windowed bwd2 kernels, one call
+            K.relpos_attn_ctx_bwd(do, ctx["o"], qu, qv, qkv, ppos, lse, lengths, dqu, dqv, dqkv, dppos, B, H, T, sc,
+                                  ctx["pa"], seed, st_att, ctx["attn_ctx"])
+            del do
+            return _attn_bwd_tail(P, G, L, ctx, dqkv, dqu, dqv, dppos, pos_emb, dx2, lng, cfg, pd, seed, salt, li, rows,
+                                  d, dev)
         if pt is None:   # bwd2
             dS, Pdr = K.attn_bwd2_saved(B, H, T, dev)
             prep = ctx.pop("attn_prep", None)
@@ -1087,7 +1126,7 @@ def encoder_forward_steps(cfg, S: EncoderShapes, P, prefix, mel, mel_len, len1, 
     # allocated (torch's per-stream pools) and written on the stream whose layers read them
     pp = pos_proj_all(cfg, P, prefix, pos_emb)
     # every layer's positional band rows for the prepared-operand attention forward in one launch
-    pbands = K.attn_band_prep(pp, S.h, S.T) if (pp is not None and _fwd3_ok(S.dk, save)) else None
+    pbands = K.attn_band_prep(pp, S.h, S.T) if (pp is not None and S.ctx is None and _fwd3_ok(S.dk, save)) else None
     bn_stats = None
     if train and bn_running is not None and use_batch_stats:
         bn_stats = ws.get("bn_stats")

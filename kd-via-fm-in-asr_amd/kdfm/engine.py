@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from . import kernels as K
-from .config import (Ver5Config, all_head_specs, bn_buffer_specs, diffkd_specs, meta_bn_specs, student_specs,
+from .config import (FULL_CONTEXT, Ver5Config, att_context, all_head_specs, bn_buffer_specs, diffkd_specs, meta_bn_specs, student_specs,
                      teacher_specs)
 from .conformer import EncoderRun, EncoderShapes, compute_lengths, encoder_backward, encoder_forward, fold_arena, \
     encoder_forward_steps, layer_images, make_workspace
@@ -98,6 +98,7 @@ class Ver5Engine:
     def __init__(self, cfg: Ver5Config, device="cuda", *, teacher_seed=0, student_seed=1, heads_seed=2,
                  init=True):
         self.cfg = cfg
+        att_context(cfg)   # validates the student's att_context_size / att_context_style (ValueError)
         self.device = torch.device(device)
         dev = self.device
         self.student = FlatStore(student_specs(cfg), dev, with_grad=True, with_adam=True)
@@ -250,7 +251,7 @@ class Ver5Engine:
         B, N = wav.shape
         Tm = mel_frames(cfg, N)
         Ss = EncoderShapes(cfg, B, Tm, cfg.d_student, cfg.heads_student)
-        St = EncoderShapes(cfg, B, Tm, cfg.d_teacher, cfg.heads_teacher)
+        St = EncoderShapes(cfg, B, Tm, cfg.d_teacher, cfg.heads_teacher, ctx=FULL_CONTEXT)   # (the frozen teacher: full context)
         T = Ss.T
         mel_len = torch.empty(B, dtype=torch.int64, device=dev)
         len1 = torch.empty_like(mel_len)

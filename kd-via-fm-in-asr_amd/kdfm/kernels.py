@@ -1837,6 +1837,91 @@ def relpos_attn_fwd(qu, qv, qkv, ppos, lengths, o, P, Pd, B, H, T, scale, p, see
             rng_stream, _s())
 
 
+def _ctx_bounds(ctx, i, T):
+    """[lo, hi] of query i's key window for the kernel triple (left, right, chunk) (csrc/attn_ctx.h)."""
+    left, right, chunk = ctx
+    if chunk > 0:
+        c = i // chunk
+        return (0 if left < 0 else max(0, (c - left) * chunk)), min(T - 1, (c + 1) * chunk - 1)
+    return (0 if left < 0 else max(0, i - left)), (T - 1 if right < 0 else min(T - 1, i + right))
+
+
+def ctx_tiles(T, ctx):
+    """(query block, key block) 64 x 64 tiles the windowed attention kernels visit per (b, h) at full length."""
+    n = 0
+    for i0 in range(0, T, 64):
+        lo, _ = _ctx_bounds(ctx, i0, T)
+        _, hi = _ctx_bounds(ctx, min(i0 + 63, T - 1), T)
+        n += hi // 64 - lo // 64 + 1
+    return n
+
+
+def _ctx_args(ctx):
+    left, right, chunk = (int(v) for v in ctx)
+    if left < -1 or right < -1 or chunk < 0:
+        raise ValueError(f"attention context triple (left, right, chunk) = {tuple(ctx)}: left / right >= -1, chunk >= 0")
+    return min(left, 1 << 30), min(right, 1 << 30), min(chunk, 1 << 30)
+
+
+def relpos_attn_ctx_fwd(qu, qv, qkv, ppos, lengths, o, B, H, T, scale, p, seed, rng_stream, ctx, lse=None):
+    """kdfm_relpos_attn_ctx_fwd: relpos_attn_fwd's single pass (o, lse) under a limited attention context
+    `ctx` = (left, right, chunk) (config.att_context_triple); key blocks outside a query block's window are
+    skipped."""
+    rows, d = qu.shape
+    assert rows == B * T and qkv.shape == (rows, 3 * d) and ppos.shape == (2 * T - 1, d) and o.shape == (rows, d)
+    assert qu.is_contiguous() and qv.is_contiguous() and qkv.is_contiguous() and ppos.is_contiguous()
+    assert o.is_contiguous() and (lse is None or (lse.shape == (B, H, T) and lse.is_contiguous()))
+    cl, cr, cc = _ctx_args(ctx)
+    fl = nb = 0.0
+    if Trace.active is not None:
+        # algorithmic: QK^T, the positional band and PV over the visited 64 x 64 tiles only; bytes as relpos_attn_fwd
+        fl = 2.0 * B * H * ctx_tiles(T, ctx) * 64 * 64 * (d // H) * 3
+        nb = 4.0 * rows * d * 5 + (4.0 * B * H * T if lse is not None else 0.0)
+    _traced("attn_fwd", fl, nb, "kdfm_relpos_attn_ctx_fwd", ptr(qu), ptr(qv), ptr(qkv), ptr(ppos), ptr(_i64(lengths)),
+            ptr(o), ptr(lse), B, H, T, d, float(scale), float(p), ptr(seed), int(rng_stream), cl, cr, cc, _s())
+
+
+def relpos_attn_ctx_bwd(do, o, qu, qv, qkv, ppos, lse, lengths, dqu, dqv, dqkv, dppos, B, H, T, scale, p, seed,
+                        rng_stream, ctx, ds=None, pd=None, ws=None):
+    """kdfm_relpos_attn_ctx_bwd: the bwd2 backward under the limited attention context `ctx` in one call
+    (dQ kernel, dK / dV over the inverse window, dPpos): dqu, dqv, dK / dV into dqkv[:, d:], dppos.  ds / pd
+    (attn_bwd2_saved) and ws (relpos_attn_bwd2_dpos_ws floats) are scratch, allocated when not given."""
+    rows, d = do.shape
+    assert rows == B * T and qkv.shape == (rows, 3 * d) and lse.shape == (B, H, T) and o.shape == do.shape
+    assert dqkv.shape == (rows, 3 * d) and dppos.shape == (2 * T - 1, d)
+    if ds is None or pd is None:
+        ds, pd = attn_bwd2_saved(B, H, T, do.device)
+    ldt = int(_lib.lib().kdfm_relpos_attn_bwd2_ldt(T))
+    assert ds.dtype == torch.bfloat16 and pd.dtype == torch.bfloat16
+    assert ds.shape == pd.shape == (B, H, T, ldt) and ds.is_contiguous() and pd.is_contiguous()
+    for t in (do, o, qu, qv, qkv, ppos, lse, dqu, dqv, dqkv, dppos):
+        assert t.is_contiguous()
+    n = relpos_attn_bwd2_dpos_ws(B, T, d)
+    if ws is None:
+        ws = scratch(do.device, n)
+    assert ws.numel() >= n
+    cl, cr, cc = _ctx_args(ctx)
+    fl = nb = 0.0
+    if Trace.active is not None:
+        # the bwd2 parts' 8 T x T products (5 dQ, 2 dK / dV, 1 dPpos) over the visited tiles; bytes: the row
+        # operands as the three bwd2 calls, dS / Pd (bf16) written once and read by dK / dV (both) and dPpos (dS)
+        tiles = ctx_tiles(T, ctx)
+        fl = 2.0 * B * H * tiles * 64 * 64 * (d // H) * 8
+        nb = 4.0 * rows * d * 13 + 4.0 * (2 * T - 1) * d + 2.0 * 5.0 * B * H * tiles * 64 * 64
+    _traced("attn_bwd", fl, nb, "kdfm_relpos_attn_ctx_bwd", ptr(do), ptr(o), ptr(qu), ptr(qv), ptr(qkv), ptr(ppos),
+            ptr(lse), ptr(_i64(lengths)), ptr(ds), ptr(pd), ptr(dqu), ptr(dqv), ptr(dqkv), ptr(dppos), ptr(ws),
+            ws.numel(), B, H, T, d, float(scale), float(p), ptr(seed), int(rng_stream), cl, cr, cc, _s())
+
+
+def relpos_softmax_ctx_fwd(ac, bd, lengths, P, Pd, B, H, T, scale, p, seed, rng_stream, ctx):
+    """relpos_softmax_fwd under the limited attention context `ctx` (the f32 parity route): masked
+    probabilities are exactly 0 in P / Pd."""
+    assert ac.numel() == B * H * T * T and bd.numel() == B * H * T * (2 * T - 1)
+    cl, cr, cc = _ctx_args(ctx)
+    call("kdfm_relpos_softmax_ctx_fwd", ptr(ac), ptr(bd), ptr(_i64(lengths)), ptr(P), ptr(Pd), B, H, T, float(scale),
+         float(p), ptr(seed), int(rng_stream), cl, cr, cc, _s())
+
+
 def attn_kv_prep(qkv, lengths, B, H, T, out=None):
     """The bf16 centred key / value tiles and the centre of kdfm_relpos_attn_fwd3 (csrc/attn_fwd3.hip):
     returns (kb, vb, centre); `out` reuses a previous triple of the same shape."""

@@ -21,7 +21,7 @@ import torch.nn as nn
 from . import _lib
 from . import kernels as K
 from .overlap import WGRAD
-from .config import Ver5Config, encoder_specs, sub_stages
+from .config import Ver5Config, att_context_triple, encoder_specs, sub_stages
 from .conformer import EncoderShapes, compute_lengths, layer_backward, layer_forward, make_workspace, \
     subsampling_backward, subsampling_forward
 from .frontend import FrontendConsts, frontend_forward, mel_frames, specaugment_
@@ -308,14 +308,37 @@ class RelPositionalEncoding(nn.Module):
 
 class ConformerEncoder(nn.Module):
     """NeMo ConformerEncoder API: forward(audio_signal (B, feat_in, T), length) -> ((B, d, T'), lengths).
-    The x*sqrt(d) scaling (xscaling) and pre-encoder dropout are fused into pre_encode's output GEMM."""
+    The x*sqrt(d) scaling (xscaling) and pre-encoder dropout are fused into pre_encode's output GEMM.
+    att_context_size / att_context_style: NeMo's limited attention context ([left, right] frames, -1 unlimited;
+    "regular" or "chunked_limited") on the windowed attention kernels; a list of several contexts
+    (multi-lookahead training), att_context_probs, rel_pos_local_attn and conv_context_size raise KdfmError."""
 
     def __init__(self, feat_in=80, n_layers=16, d_model=176, n_heads=4, subsampling="striding",
                  subsampling_factor=4, subsampling_conv_channels=-1, causal_downsampling=False, ff_expansion_factor=4,
                  self_attention_model="rel_pos", conv_kernel_size=31, dropout=0.1, dropout_pre_encoder=0.1,
                  dropout_emb=0.0, dropout_att=0.1, xscaling=True, untie_biases=True, pos_emb_max_len=5000,
-                 conv_norm_type="batch_norm", device=None, init_seed=0, **_):
+                 conv_norm_type="batch_norm", att_context_size=None, att_context_style="regular",
+                 att_context_probs=None, conv_context_size=None, device=None, init_seed=0, **_):
         super().__init__()
+        if self_attention_model == "rel_pos_local_attn":
+            raise _lib.KdfmError("kdfm ConformerEncoder: self_attention_model='rel_pos_local_attn' (Longformer-style "
+                                 "local attention) is not implemented; use rel_pos with att_context_size")
+        if att_context_probs is not None:
+            raise _lib.KdfmError("kdfm ConformerEncoder: att_context_probs (multi-lookahead training) is not implemented")
+        if conv_context_size is not None:
+            raise _lib.KdfmError("kdfm ConformerEncoder: conv_context_size (causal / limited convolutions) is not "
+                                 "implemented; only None")
+        if att_context_size is None:
+            att_context_size = (-1, -1)
+        att_context_size = list(att_context_size)
+        if att_context_size and isinstance(att_context_size[0], (list, tuple)):
+            if len(att_context_size) != 1:
+                raise _lib.KdfmError("kdfm ConformerEncoder: a list of several att_context_size entries "
+                                     "(multi-lookahead training) is not implemented")
+            att_context_size = list(att_context_size[0])
+        if len(att_context_size) != 2:
+            raise ValueError(f"att_context_size must be [left, right], got {att_context_size!r}")
+        att_context_triple(att_context_size, att_context_style)   # ValueError for the reference's invalid combinations
         if self_attention_model != "rel_pos" or conv_norm_type != "batch_norm" or not untie_biases \
                 or (subsampling == "striding" and subsampling_conv_channels not in (-1, d_model)):
             raise _lib.KdfmError("kdfm ConformerEncoder implements the Conformer-CTC / FastConformer recipes "
@@ -324,7 +347,9 @@ class ConformerEncoder(nn.Module):
                               conv_kernel=conv_kernel_size, dropout=dropout, dropout_pre=dropout_pre_encoder,
                               dropout_att=dropout_att, subsampling=subsampling, subsampling_factor=subsampling_factor,
                               subsampling_conv_channels=subsampling_conv_channels,
-                              causal_downsampling=causal_downsampling, xscaling=xscaling)
+                              causal_downsampling=causal_downsampling, xscaling=xscaling,
+                              att_context_size=tuple(int(v) for v in att_context_size),
+                              att_context_style=att_context_style)
         sub_stages(self.cfg)   # validates the subsampling choice
         self.d_model, self.n_heads = d_model, n_heads
         self._feat_out = d_model

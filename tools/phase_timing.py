@@ -40,7 +40,7 @@ for rep in range(2):
     dev = eng.device
     Tm = mel_frames(cfg, N)
     Ss = EncoderShapes(cfg, B, Tm, cfg.d_student, cfg.heads_student)
-    St = EncoderShapes(cfg, B, Tm, cfg.d_teacher, cfg.heads_teacher)
+    St = EncoderShapes(cfg, B, Tm, cfg.d_teacher, cfg.heads_teacher, ctx=(-1, -1, 0))
     T = Ss.T
     mel_len = torch.empty(B, dtype=torch.int64, device=dev)
     len1, len2 = torch.empty_like(mel_len), torch.empty_like(mel_len)
